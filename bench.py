@@ -25,6 +25,12 @@ with world_size 1, broadcast, all-reduce of the flat gradient bucket inside the 
 
 The batches come from the product's own on-device batch builder (RayGeneratorHip: synthetic cameras, random images and visibility
 priors, rays generated on the GPU); `oracle/` is imported for the `cpu_baseline` leg only.
+
+A plain run measures `value` alone: set-up, 2 initialisation passes, W warm-up steps, ONE timed region of exactly K steps (per-kernel
+events off), the line.  Everything else described above -- the other arithmetics, `roofline`, the render leg, `configs4_dtu`,
+`configs2_realestate`, `sizes`, `cpu_baseline`, the multi-rank self-check, the median of `--repeats` timed regions and the full report --
+runs with `--full`.  `--dump-outputs DIR` writes what the last timed step returned to its caller (model outputs, losses, updated
+parameters, gradients) as DIR/<name>.npy; the inputs of a run are a function of its arguments only.
 """
 import argparse
 import json
@@ -354,9 +360,10 @@ def compact_line(full: dict) -> dict:
     cf = full.get('config', {})
     c['config'] = {k: cf[k] for k in ('workload', 'rays_per_gpu', 'global_rays', 'parallelism', 'gemm_arithmetic', 'collectives') if k in cf}
     r = full.get('roofline') or {}
-    c['roofline'] = {k: _short(r[k]) for k in ('bound', 'kernel', 'achieved', 'peak', 'unit', 'frac', 'avg_launch_ms', 'launches_per_step', 'step_frac',
-                                              'sclk_mhz', 'traffic', 'traffic_ratio', 'algorithmic_bytes_per_step', 'traffic_source',
-                                              'traffic_profile_is_of_current_kernels') if k in r}
+    if r:                                             # (a plain run has none: --full)
+        c['roofline'] = {k: _short(r[k]) for k in ('bound', 'kernel', 'achieved', 'peak', 'unit', 'frac', 'avg_launch_ms', 'launches_per_step', 'step_frac',
+                                                  'sclk_mhz', 'traffic', 'traffic_ratio', 'algorithmic_bytes_per_step', 'traffic_source',
+                                                  'traffic_profile_is_of_current_kernels') if k in r}
     for g, st in (r.get('stages') or {}).items():
         c['roofline']['ms_' + g] = st['ms_per_step']
         if 'frac_executed' in st:
@@ -409,6 +416,56 @@ def compact_line(full: dict) -> dict:
     return c
 
 
+DUMP_LIMIT = 64 * 10 ** 6       # bytes of --dump-outputs in all, the files' headers included
+NPY_HEADER = 512                # what one .npy header may take (np.save pads it to a multiple of 64 bytes)
+
+
+def host_arrays(tree, prefix=''):
+    """{name: numpy array} of every tensor / number in a (nested) dict of step results, as the caller holds them: floating point as float32
+    (float64 stays float64), integers and flags as float64.  Other members (names, lists) are left out."""
+    import numpy as np
+    out = {}
+    for k, v in tree.items():
+        name = prefix + str(k)
+        if isinstance(v, dict):
+            out.update(host_arrays(v, name + '.'))
+        elif isinstance(v, torch.Tensor):
+            v = v.detach()
+            v = v.double() if not v.is_floating_point() or v.dtype == torch.float64 else v.float()
+            out[name] = v.cpu().numpy()
+        elif isinstance(v, (bool, int, float)):
+            out[name] = np.asarray(v, dtype=np.float64)
+    return out
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT):
+    """--dump-outputs: every array as <out_dir>/<name>.npy.  Over `limit` bytes in all, every array of more than one row keeps a fixed, seeded
+    sample of its rows (the same rows from run to run for the same shapes), so that the files stay within `limit`.  -> bytes written"""
+    import re
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    limit -= NPY_HEADER * len(arrays)
+    if total > limit:
+        rng = np.random.default_rng(0)
+        small = sum(a.nbytes for a in arrays.values() if a.ndim == 0 or a.shape[0] <= 1)
+        frac = max(limit - small, 0) / max(total - small, 1)
+        for name in sorted(arrays):
+            a = arrays[name]
+            if a.ndim and a.shape[0] > 1:
+                rows = np.sort(rng.choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False))
+                arrays[name] = a[rows]
+        total = sum(a.nbytes for a in arrays.values())
+    assert total <= limit, 'bench.py: %d bytes of outputs do not fit --dump-outputs\' %d' % (total, limit)
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, re.sub(r'[^\w.-]', '_', name) + '.npy')
+        np.save(path, a)
+        written += os.path.getsize(path)
+    assert written <= limit + NPY_HEADER * len(arrays), written
+    return written
+
+
 def respawn_cmd(gpus, environ, argv):
     """The launcher command `python bench.py --gpus N` turns itself into when N > 1 and no launcher set WORLD_SIZE, else None.
     Raises SystemExit when a launcher's WORLD_SIZE contradicts --gpus."""
@@ -456,13 +513,19 @@ def main():
                     'contract (model() -> compute_losses -> backward -> optimizer.step, Trainer01.py:61-107); onecall = vipnerf_train_step')
     ap.add_argument('--report-path', default=None, help='where the full report goes (default: gpurun_out/bench_full.json when gpurun_out/ exists, else '
                     'bench_full.json next to bench.py); the line names it in `full_report`')
-    ap.add_argument('--repeats', type=int, default=3, help='timed regions of K steps each for `value` (and the --also arithmetics): the line reports the MEDIAN '
-                    'run (its K steps, its ms_per_step); every run is in the full report under `runs_ms_per_step`')
+    ap.add_argument('--repeats', type=int, default=None, help='timed regions of K steps each for `value` (and the --also arithmetics): the line reports the MEDIAN '
+                    'run (its K steps, its ms_per_step); every run is in the full report under `runs_ms_per_step` (default 3 with --full, else 1)')
     ap.add_argument('--verify-rows', type=int, default=None, help='rows of the self-check\'s global batch (default: rays per GPU x ranks); lets ONE GPU run the '
                     'check at the size an 8-GPU run gives it (tests/test_hip_dist.py)')
     ap.add_argument('--check-ranks', action='store_true', help='spawn / join the ranks, count them with one all-reduce, print {"n_gpus", "ranks_reduced"} '
                     'and exit without touching a GPU (the CPU test of the --gpus N launcher)')
+    ap.add_argument('--full', action='store_true', help='everything beyond `value`: the --also arithmetics, roofline, render, configs4 / configs2 '
+                    'blocks, sizes, CPU baseline, the multi-rank self-check, --repeats timed regions and the full report (a plain run times `value` only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last one returned (model outputs, '
+                    'losses, updated parameters, gradients) as DIR/<name>.npy, float32 / float64, %d MB at most' % (DUMP_LIMIT // 10 ** 6))
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it: become the launcher (one rank per GPU under torch.distributed.run).  A
     # WORLD_SIZE that contradicts --gpus is an error: the line never reports an n_gpus other than the number of ranks that reduced.
@@ -556,6 +619,7 @@ def main():
                 b['rng_ray_base'] = rank * self.rows   # keyed by global ray index)
             torch.cuda.synchronize()
             self.it = 40000
+            self.keep, self.kept, self.outputs = False, None, None
 
         def step(self, i):
             src = self.batches[i % self.n_batches]
@@ -564,7 +628,9 @@ def main():
             b['iter_num'] = self.it                   # a new iteration number per step: new Philox offset (loss weights: > 30000)
             self.it += 1
             if self.stepper is not None:
-                self.stepper(b)
+                res = self.stepper(b)
+                if self.keep:                         # (references only: copied to the host after the timed region)
+                    self.kept = {'out': dict(self.stepper.outputs), 'loss': res}
                 return
             self.bucket.release()
             out = self.model(b)
@@ -572,13 +638,24 @@ def main():
             losses['TotalLoss'].backward()
             self.bucket.all_reduce_mean()
             self.opt.step()
+            if self.keep:
+                self.kept = {'out': {k: v.detach() if isinstance(v, torch.Tensor) else v for k, v in out.items()},
+                             'loss': {k: v.detach() if isinstance(v, torch.Tensor) else v for k, v in losses.items()}}
 
-        def timed_run(self, prec, profile=True, repeats=1):
+        def take_outputs(self):
+            """What the kept step handed its caller, on the host: its outputs and losses, then the parameters it updated and their gradients."""
+            tree = dict(self.kept, param=dict(self.model.named_parameters()),
+                        grad={n: p.grad for n, p in self.model.named_parameters() if p.grad is not None})
+            self.kept = None
+            return host_arrays(tree)
+
+        def timed_run(self, prec, profile=True, repeats=1, keep_outputs=False):
             """The contract's procedure for one arithmetic: [2 untimed initialisation passes: kernel loading, the caching
             allocator's multi-GB workspace blocks, Adam's state] W warm-up steps, then EXACTLY K steps between barrier +
             synchronize pairs; max over ranks.  repeats > 1: that timed region `repeats` times back to back (each its own barrier pair and K
             steps); the run reported is the MEDIAN one -- its elapsed time, its per-kernel events, its collective times -- and every run's
-            ms per step is kept in self.last_runs (box noise of +- 0.15 ms per step is as large as a kernel change worth keeping)."""
+            ms per step is kept in self.last_runs (box noise of +- 0.15 ms per step is as large as a kernel change worth keeping).
+            keep_outputs: what the last step of the last timed region returned goes to self.outputs (host arrays, copied after the region)."""
             self.model.configs['model']['hip_precision'] = prec
             if self.stepper is not None:
                 self.stepper.release()               # the one-call path's persistent buffers of the previous arithmetic
@@ -595,7 +672,9 @@ def main():
                 barrier()
                 t0 = time.perf_counter()
                 for i in range(args.steps):
+                    self.keep = keep_outputs and rep == max(1, repeats) - 1 and i == args.steps - 1
                     self.step(args.warmup + rep * args.steps + i)
+                self.keep = False
                 torch.cuda.synchronize()
                 own = time.perf_counter() - t0           # this rank's own K steps (before the closing barrier): min / max over ranks attribute a slow rank
                 barrier()
@@ -609,6 +688,8 @@ def main():
                          'rank_ms_per_step_min': round(-max_over_ranks(-own) / args.steps * 1e3, 3),
                          'rank_ms_per_step_max': round(max_over_ranks(own) / args.steps * 1e3, 3)}
                 runs.append((elapsed, prof, extra))
+            if self.kept is not None:
+                self.outputs = self.take_outputs()
             order = sorted(range(len(runs)), key=lambda j: runs[j][0])     # (elapsed is already the max over ranks: every rank picks the same run)
             elapsed, prof, self.last_extra = runs[order[(len(runs) - 1) // 2]]
             self.last_runs = [round(r[0] / args.steps * 1e3, 3) for r in runs]
@@ -674,14 +755,19 @@ def main():
     model = main_wl.model
     # N > 1 (or --force-dist): the scaling line carries its own parity evidence -- the reduced sharded gradient against the whole-batch gradient
     # BEFORE the timed region, bit-identical parameters on every rank AFTER it; a failure is reported in the line and the run exits non-zero
-    verify = main_wl.verify_sharding(args.precision) if collectives else None
-    elapsed, prof, sclk = main_wl.timed_run(args.precision, repeats=args.repeats)
+    # (--full only, like every block below that is not `value` itself: a plain run times `value` and prints its line)
+    check = collectives and args.full
+    verify = main_wl.verify_sharding(args.precision) if check else None
+    elapsed, prof, sclk = main_wl.timed_run(args.precision, profile=args.full, repeats=args.repeats, keep_outputs=bool(args.dump_outputs))
     main_extra, main_runs = main_wl.last_extra, main_wl.last_runs
-    same = vdist.params_identical(model.parameters()) if collectives else None
-    verify_failed = bool(collectives and (not (verify['rel_l2'] <= GRAD_SHARD_TOL) or not same['identical']))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(main_wl.outputs, args.dump_outputs)
+    main_wl.outputs = None
+    same = vdist.params_identical(model.parameters()) if check else None
+    verify_failed = bool(check and (not (verify['rel_l2'] <= GRAD_SHARD_TOL) or not same['identical']))
     # N > 1 (the driver's scaling runs): `value` plus the configs[4] arithmetic only, unless --also is given explicitly
     also_arg = args.also if (world == 1 or '--also' in sys.argv) else 'bf16'
-    also = [] if args.no_other_precisions else \
+    also = [] if args.no_other_precisions or not args.full else \
         ([p for p in ARITH if p != args.precision] if also_arg == 'all' else [p for p in also_arg.split(',') if p and p != args.precision])
     others, other_runs = {}, {}
     for p in also:
@@ -721,12 +807,12 @@ def main():
         model.train()
         return render
 
-    render = None if args.no_render else render_bench()          # every rank: its strip of the frame
+    render = None if args.no_render or not args.full else render_bench()          # every rank: its strip of the frame
 
     # BASELINE configs[4] at its per-GPU shard size, every rank its own 16,384 rays: at N = 8 this IS configs[4]'s statement (131,072 rays
     # per iteration ray-sharded over 8 GPUs, one all-reduce per step); `--workload dtu --scaling strong --precision bf16` puts it into `value`
     c4 = None
-    if not args.no_configs4 and not (args.workload == 'dtu' and rays == args.configs4_rays):
+    if args.full and not args.no_configs4 and not (args.workload == 'dtu' and rays == args.configs4_rays):
         main_wl.release()
         wl4 = Workload('dtu', args.configs4_rays, 'bf16')
         c4 = {'workload': 'BASELINE configs[4] per-GPU shard: DTU geometry (non-NDC), 3 views (V = 2 secondary views), 131,072 / 8 = %d rays/iter x '
@@ -743,7 +829,7 @@ def main():
     # BASELINE configs[2]: RealEstate geometry, 3 input views (V = 2), visibility + sparse-depth priors: the reference's batch of 2048 nerf rows
     # + 2048 sparse-depth rows (RealEstateTrainerTester01.py:249-259; SparseDepthMSE at weight 0.1, SparseDepthMSE01.py:58-63), every rank its own batch
     c2 = None
-    if not args.no_configs2 and not (args.workload == 'realestate'):
+    if args.full and not args.no_configs2 and not (args.workload == 'realestate'):
         if c4 is None:
             main_wl.release()
         wl2 = Workload('realestate', 2048, 'fp32', n_sparse=2048)
@@ -761,7 +847,7 @@ def main():
     # NerfLlffTrainerTester01.py:251,261,617), through the module contract AND through the one-call step (vipnerf_train_step): at these
     # sizes the 16-bit step is as long as the host needs to enqueue it through five Python -> ctypes calls
     sizes = None
-    if not args.no_sizes and world == 1:
+    if args.full and not args.no_sizes and world == 1:
         if c4 is None and c2 is None:
             main_wl.release()
         sizes = {'note': 'ms per training step (K timed steps, same procedure as `value`); module = VipNeRFHip.forward -> compute_losses -> backward -> '
@@ -800,7 +886,7 @@ def main():
                    'gemm_arithmetic': args.precision, 'arithmetic_note': ARITH[args.precision][3],
                    'optimizer': 'Adam(lr 5e-4, betas 0.9 / 0.999): ' + ('vipnerf_hip.optim.FlatAdam -- torch.optim.Adam\'s single-tensor update on one flat '
                                  'parameter / moment / gradient buffer, one launch (vipnerf_adam_step; bit-identical per parameter)' if args.optimizer == 'flat' else 'torch.optim.Adam(fused=True)')},
-        'roofline': roofline_block(args.precision, prof, args.steps, rays, ms, sclk, n_sec=n_sec, workload=args.workload),
+        'roofline': roofline_block(args.precision, prof, args.steps, rays, ms, sclk, n_sec=n_sec, workload=args.workload) if args.full else None,
         'runs_ms_per_step': main_runs, 'runs_reported': 'median of %d timed regions of %d steps' % (len(main_runs), args.steps),
     }
     if collectives and world == 1:
@@ -826,6 +912,7 @@ def main():
     result['step_api'] = args.step_api
     if collectives:
         result.update({k: v for k, v in main_extra.items() if v is not None})
+    if check:
         result['grad_allreduce_vs_whole_batch'] = float('%.3e' % verify['rel_l2'])
         result['ranks_param_identical'] = same['identical']
         result['sharding_check'] = dict(verify, tolerance=GRAD_SHARD_TOL, global_rows=args.verify_rows or (rays + main_wl.n_sparse) * world, params=same,
@@ -841,9 +928,16 @@ def main():
     except Exception:
         pass
 
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import vipnerf_oracle as vo       # the checker, as the reported CPU baseline only
         result['cpu_baseline'] = cpu_baseline(vo, n_rays=args.cpu_rays)
+    if not args.full:                             # a plain run: the line alone, no report
+        result.pop('roofline')
+        os.write(json_fd, (json.dumps(compact_line(result), separators=(',', ':')) + '\n').encode())
+        if torch.distributed.is_initialized():
+            vdist.barrier()
+            torch.distributed.destroy_process_group()
+        return
     result['notes'] = NOTES
     # the full report: a file next to bench.py (and under gpurun_out/ when that exists) and stderr; stdout gets ONE compact line
     report_path = args.report_path or os.path.join(ROOT, 'gpurun_out' if os.path.isdir(os.path.join(ROOT, 'gpurun_out')) else '', 'bench_full.json')

@@ -106,15 +106,33 @@ def ref_batch(b, iter_num):
     return rb
 
 
+PART_BYTES = 900 << 10     # a fixture with more array bytes is written as <name>.part<i>.npz files (no committed file reaches 1 MiB)
+
+
+def split_parts(out: dict):
+    """The arrays of one fixture in key order, cut into consecutive groups of at most PART_BYTES (a larger array alone)."""
+    parts, cur, size = [], {}, 0
+    for k, v in out.items():
+        if cur and size + v.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += v.nbytes
+    return parts + [cur]
+
+
 def npz(name, **arrs):
     out = {}
     for k, v in arrs.items():
         if isinstance(v, torch.Tensor):
             v = v.detach().cpu().numpy()
         out[k] = np.asarray(v)
-    path = os.path.join(GOLD, name + '.npz')
-    np.savez_compressed(path, **out)
-    print('%-34s %8.1f KB' % (name + '.npz', os.path.getsize(path) / 1024))
+    parts = split_parts(out)
+    for i, part in enumerate(parts):
+        fname = name + ('.part%d' % i if len(parts) > 1 else '') + '.npz'
+        path = os.path.join(GOLD, fname)
+        np.savez_compressed(path, **part)
+        print('%-34s %8.1f KB' % (fname, os.path.getsize(path) / 1024))
 
 
 def digest(t: torch.Tensor):

@@ -98,3 +98,41 @@ def test_compact_line_falls_back_to_the_bare_contract():
             assert c['grad_allreduce_vs_whole_batch'] == 2.5e-6 and c['ranks_param_identical'] is True and c['ranks_reduced'] == 8
         else:
             assert c['cpu_baseline']['value'] == full['cpu_baseline']['value']
+
+
+def test_plain_line_is_the_contract_without_the_full_report():
+    """A plain run (no --full) has no roofline and no report: its line is the contract's keys and the scalars it measured."""
+    import bench
+    full = _canned(1)
+    plain = {k: full[k] for k in CONTRACT}
+    plain.update(ranks_reduced=1, step_api='module', build_info_sha16='0123456789abcdef')
+    c = bench.compact_line(plain)
+    assert 'roofline' not in c and 'cpu_baseline' not in c and 'full_report' not in c
+    for k in CONTRACT:
+        assert c[k] == plain[k] if k != 'config' else k in c
+    assert c['ms_per_step'] == full['ms_per_step'] and c['metric'] == 'train_rays_per_sec'
+
+
+def test_dump_outputs_types_names_and_seeded_sample(tmp_path):
+    """--dump-outputs: float32 / float64 files named after the step's results; over the limit every array keeps the same seeded rows."""
+    import numpy as np
+    import torch
+    import bench
+    tree = {'out': {'rgb_fine': torch.rand(4096, 3), 'z_vals_fine': torch.rand(4096, 192, dtype=torch.float64), 'ids': torch.arange(4096),
+                    'half': torch.ones(8, dtype=torch.bfloat16), 'names': ['a']},
+            'loss': {'TotalLoss': torch.tensor(0.5), 'n': 3}, 'param': {'fine_model.pts_linears.0.weight': torch.rand(256, 63)}}
+    arrs = bench.host_arrays(tree)
+    assert sorted(arrs) == ['loss.TotalLoss', 'loss.n', 'out.half', 'out.ids', 'out.rgb_fine', 'out.z_vals_fine', 'param.fine_model.pts_linears.0.weight']
+    assert arrs['out.ids'].dtype == np.float64 and arrs['out.half'].dtype == np.float32 and arrs['out.z_vals_fine'].dtype == np.float64
+    n0 = bench.dump_outputs(dict(arrs), str(tmp_path / 'a'))
+    assert n0 == sum(os.path.getsize(tmp_path / 'a' / f) for f in os.listdir(tmp_path / 'a')) and n0 > sum(a.nbytes for a in arrs.values())
+    assert np.array_equal(np.load(tmp_path / 'a' / 'out.rgb_fine.npy'), arrs['out.rgb_fine'])
+    limit = 1 << 20
+    n1 = bench.dump_outputs(dict(arrs), str(tmp_path / 'b'), limit=limit)
+    bench.dump_outputs(dict(arrs), str(tmp_path / 'c'), limit=limit)
+    assert n1 <= limit and n1 == sum(os.path.getsize(tmp_path / 'b' / f) for f in os.listdir(tmp_path / 'b'))
+    for f in os.listdir(tmp_path / 'b'):
+        a, b = np.load(tmp_path / 'b' / f), np.load(tmp_path / 'c' / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    assert np.load(tmp_path / 'b' / 'out.ids.npy').shape[0] < 4096
+    assert np.array_equal(np.load(tmp_path / 'b' / 'loss.TotalLoss.npy'), arrs['loss.TotalLoss'])

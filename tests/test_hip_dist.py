@@ -93,15 +93,7 @@ def test_eight_hip_ranks_on_one_gpu_equal_one_process():
     assert torch.cuda.is_available()
     world, port = 8, 30000 + (os.getpid() % 900)
     ret = mp.Manager().dict()
-    try:
-        mp.spawn(_worker, args=(world, port, ret), nprocs=world, join=True)
-    except mp.ProcessExitedException as e:
-        # eight processes SHARING one device: about one start in twenty-five a rank's queue is aborted by the runtime (see
-        # test_bench_self_spawns_eight_ranks_strong_scaling and profiles/r05_spawn8_abort.log); such a start is repeated once, on another port
-        import warnings
-        warnings.warn(f'a rank died while eight processes opened the device ({e}); repeating the launch once')
-        ret = mp.Manager().dict()
-        mp.spawn(_worker, args=(world, port + 901, ret), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, port, ret), nprocs=world, join=True)     # (a rank that dies fails the test: no second launch after a fault)
     from oracle import vipnerf_oracle as vo
     import test_hip_parity as tp
     dev = torch.device('cuda:0')
@@ -131,19 +123,8 @@ def test_bench_self_spawns_eight_ranks_strong_scaling():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env['VIPNERF_DIST_BACKEND'] = 'gloo'
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--scaling', 'strong', '--global-rays', '8192',
-           '--no-configs4', '--no-configs2', '--also', 'bf16']
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
-    if r.returncode != 0 and 'Signal 6 (SIGABRT)' in r.stderr:
-        # eight HIP processes SHARING one device: about one start in twenty-five a rank dies by SIGABRT.  Round 5 ran the start 24 times
-        # with the runtime's log on (tools/spawn8_bench_probe.sh, profiles/r05_spawn8_abort.log): the rank's hardware queue is aborted with
-        # HSA_STATUS_ERROR_ILLEGAL_INSTRUCTION while the dispatch in flight is PyTorch's own FillFunctor kernel (a torch.zeros of the
-        # 1.19 M-float gradient bucket) -- not one of this library's kernels -- and 320 single-GPU process starts that load the library and run
-        # its forward kernel never showed it (tools/spawn8_probe.py): the runtime under eight processes on one device, not the code under
-        # test.  The statement under test is bench.py's launcher and rank accounting, so such a start is repeated once -- a second abort
-        # fails the test.  (On a real 8-GPU node every rank owns its device.)
-        import warnings
-        warnings.warn('a rank aborted while eight processes opened the device; repeating the launch once')
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+           '--full', '--no-configs4', '--no-configs2', '--also', 'bf16']
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)      # (a rank that dies fails the test: no second launch)
     if r.returncode != 0:            # what the failing rank itself said sits far above the launcher's summary
         import re
         told = [ln for ln in r.stderr.splitlines() if re.search(r'abort|terminate|what\(\)|HSA_|hipError|HIP error|Assertion|Segmentation|memory|Traceback|Error:', ln)]
@@ -176,7 +157,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, VIPNERF_DIST_BACKEND='gloo')
     port = 32000 + (os.getpid() % 2000)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--configs4-rays', '512',
+           '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full', '--configs4-rays', '512',
            '--rays', '1024']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -369,7 +350,7 @@ def test_bench_force_dist_single_rank_rccl():
     import subprocess
     env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(34000 + (os.getpid() % 2000)), HSA_ENABLE_IPC_MODE_LEGACY='0')
     env.pop('VIPNERF_DIST_BACKEND', None)
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--force-dist', '--steps', '3', '--warmup', '1', '--rays', '1024', '--also', '',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--force-dist', '--steps', '3', '--warmup', '1', '--rays', '1024', '--full', '--also', '',
            '--no-cpu-baseline', '--no-render']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -390,7 +371,7 @@ def test_bench_self_check_at_the_eight_gpu_global_batch_size():
     env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(36000 + (os.getpid() % 2000)), HSA_ENABLE_IPC_MODE_LEGACY='0')
     env.pop('VIPNERF_DIST_BACKEND', None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--force-dist', '--verify-rows', '32768', '--steps', '2', '--warmup', '1', '--repeats', '1',
-           '--also', '', '--no-cpu-baseline', '--no-render', '--no-configs4', '--no-configs2', '--no-sizes']
+           '--full', '--also', '', '--no-cpu-baseline', '--no-render', '--no-configs4', '--no-configs2', '--no-sizes']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])

@@ -141,7 +141,7 @@ def test_bench_line_verifies_itself_on_distinct_devices():
     world = WORLDS[-1]
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR', 'VIPNERF_DIST_BACKEND')}
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--steps', '3', '--warmup', '1', '--rays', '1024',
-                        '--no-configs4', '--no-configs2', '--no-render', '--repeats', '1'], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        '--full', '--no-configs4', '--no-configs2', '--no-render', '--repeats', '1'], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])
     assert res['n_gpus'] == world and res['ranks_reduced'] == world

@@ -33,7 +33,8 @@ REF_NAMES = {'MSEHip01': 'MSE01', 'VisibilityLossHip01': 'VisibilityLoss01', 'Vi
 
 
 def _load():
-    return {k: v for k, v in np.load(os.path.join(ROOT, 'tests', 'golden', 'f9_trajectory_fern.npz')).items()}
+    import test_oracle_golden                # (its loader joins the fixture's .part<i>.npz files)
+    return test_oracle_golden.load('f9_trajectory_fern')
 
 
 def _digest(t):

@@ -57,7 +57,9 @@ def test_learning_rate_and_loss_weight_follow_the_reference_trajectory():
     """F9 (the reference's lr decayer and LossComputer weights over iterations 29996..30003): the host logic that needs no GPU."""
     import numpy as np
     from vipnerf_hip.step import loss_weight
-    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'f9_trajectory_fern.npz'))
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import test_oracle_golden                # (its loader joins the fixture's .part<i>.npz files)
+    g = test_oracle_golden.load('f9_trajectory_fern')
     tr = _trainer(1, 1, ())
     first = int(g['first_iter'])
     lc = {'name': 'VisibilityPriorLossHip01', 'iter_weights': {'0': 0, '30000': 0.001}}

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/round
 mkdir -p $OUT
 if [ -z "$SKIP_TESTS" ]; then
 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; tail -1 $OUT/pytest_gpu.log
-python bench.py > $OUT/bench.json.log 2> $OUT/bench.err; tail -c 600 $OUT/bench.json.log
+python bench.py --full > $OUT/bench.json.log 2> $OUT/bench.err; tail -c 600 $OUT/bench.json.log
 fi
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_ks && rocprofv3 --kernel-trace --stats -d /tmp/prof_ks -- python $ROOT/bench.py --steps 5 --warmup 2 --precision $PREC --no-cpu-baseline --no-render --no-other-precisions --no-configs4 --no-configs2 --no-sizes --repeats 1 > /tmp/prof_ks.log 2>&1
