@@ -343,7 +343,9 @@ int32_t vipnerf_adam_step(int64_t n, float *param, float *exp_avg, float *exp_av
  * synchronisation, no allocation: every buffer is the caller's and may be reused from call to call.
  *
  * cfg: train and save_acts must be set.  rays->rays_o2 may be produced by the call itself: give poses / pixel_id / n_frames and a
- * rays_o2_out buffer (N, n_frames-1, 3) that rays->rays_o2 points to (vipnerf_secondary_origins), or leave poses NULL.
+ * rays_o2_out buffer (N, n_frames-1, 3) that rays->rays_o2 points to (vipnerf_secondary_origins), or leave poses NULL.  (The coarse-depth
+ * launch writes them when a ray has at least 3 (n_frames-1) coarse samples; below that, vipnerf_secondary_origins runs in front.)
+ * A 16-bit level whose rays x samples is not a multiple of 32 is refused before any launch: parameters and Adam state are untouched.
  * loss_weights[k]: weight of lout->loss_values[k] in TotalLoss (LossComputer01.py:33-44; 0 for a loss that is not configured).
  * The seed arrays of `lout` hold the WEIGHTED seeds afterwards.  grads_*: dLoss/dparam, overwritten (24 + 24 views of one flat buffer
  * when an optimizer step or an all-reduce follows).  adam_n > 0: the update of vipnerf_adam_step on the flat buffers after the backward

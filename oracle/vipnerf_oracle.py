@@ -25,7 +25,8 @@ Reference lines each function follows (paths relative to /root/reference/):
   total_loss             src/loss_functions/LossComputer01.py:33-69
 
 Differences from the reference that are deliberate: random numbers are *inputs* (`rng` dict with `t_rand`
-(N,Sc), `u` (N,Sf), `noise_coarse` (N,Sc), `noise_fine` (N,Sc+Sf)) instead of draws on the CPU generator;
+(N,Sc), `u` (N,Sf), `noise_coarse` (N,Sc), `noise_fine` (N,Sc+Sf); optionally `z_coarse` / `z_fine`, teacher-forced depths) instead of
+draws on the CPU generator;
 there is no chunk/netchunk host loop unless `chunk` is given (it changes nothing numerically except the
 GEMM blocking inside the BLAS).
 """
@@ -94,8 +95,10 @@ def init_params(seed: int, depth: int = 8, width: int = 256, l_pts: int = 10, l_
     return out
 
 
-def params_to_torch(params: Dict[str, np.ndarray], requires_grad: bool = False) -> Dict[str, torch.Tensor]:
-    return {k: torch.tensor(v, dtype=torch.float32, requires_grad=requires_grad) for k, v in params.items()}
+def params_to_torch(params: Dict[str, np.ndarray], requires_grad: bool = False, dtype=torch.float32) -> Dict[str, torch.Tensor]:
+    """dtype=torch.float64: the float32 values upcast exactly (the float64 restatement of tests/rows_f64.py); every function below
+    computes in the dtype of its inputs -- no constant or intermediate of theirs is made in the default dtype."""
+    return {k: torch.tensor(v, dtype=dtype, requires_grad=requires_grad) for k, v in params.items()}
 
 
 # ----------------------------------------------------------------------------------------------- encoding / MLP
@@ -162,7 +165,7 @@ def mlp_forward(p: Dict[str, torch.Tensor], level: str, pts: torch.Tensor, view_
 def coarse_depths(near: torch.Tensor, far: torch.Tensor, n_samples: int, t_rand: Optional[torch.Tensor],
                   lindisp: bool = False) -> torch.Tensor:
     """near, far (N,1) -> (N,S).  t_rand (N,S) in [0,1) switches stratified jitter on."""
-    tau = torch.linspace(0., 1., steps=n_samples)
+    tau = torch.linspace(0., 1., steps=n_samples, dtype=near.dtype)
     if lindisp:
         z = 1. / (1. / near * (1. - tau) + 1. / far * tau)
     else:
@@ -197,7 +200,7 @@ def fine_depths(z_coarse: torch.Tensor, w_coarse: torch.Tensor, n_fine: int, u: 
     """-> z_fine (N,Sc+Sf) ascending, inds (N,Sf), samples (N,Sf).  u=None -> deterministic linspace."""
     mid = .5 * (z_coarse[:, 1:] + z_coarse[:, :-1])
     if u is None:
-        u = torch.linspace(0., 1., steps=n_fine).expand(z_coarse.shape[0], n_fine)
+        u = torch.linspace(0., 1., steps=n_fine, dtype=z_coarse.dtype).expand(z_coarse.shape[0], n_fine)
     samples, inds = sample_pdf(mid, w_coarse[:, 1:-1], u)
     samples = samples.detach()
     z, _ = torch.sort(torch.cat([z_coarse, samples], dim=-1), dim=-1)
@@ -219,7 +222,7 @@ def secondary_dirs(z: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor, 
 def ndc_to_metric_depth(z_ndc: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor) -> torch.Tensor:
     oz, dz = rays_o[:, 2:3], rays_d[:, 2:3]
     tn = -(1 + oz) / dz
-    c = torch.where(z_ndc == 1., 1e-3, 0.)
+    c = torch.where(z_ndc == 1., torch.full_like(z_ndc, 1e-3), torch.zeros_like(z_ndc))
     return (oz + tn * dz) / dz * (1 / (1 - z_ndc + c) - 1) + tn
 
 
@@ -302,7 +305,10 @@ def render_rays(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg:
 
     def level_pass(level, z, noise):
         n, s = z.shape
-        pts = (o_s[:, None, :] + d_s[:, None, :] * z[..., None]).reshape(-1, 3)
+        if cfg.get('points_f32'):     # the sample positions as float32 arithmetic forms them (o + z d), upcast: the positional encoding's 2^9 x
+            pts = (o_s.float()[:, None, :] + d_s.float()[:, None, :] * z.float()[..., None]).to(z.dtype).reshape(-1, 3)   # amplifies their rounding
+        else:
+            pts = (o_s[:, None, :] + d_s[:, None, :] * z[..., None]).reshape(-1, 3)
         vd = vdir[:, None, :].expand(n, s, 3).reshape(-1, 3)
         vd2 = None
         if o2 is not None:
@@ -330,6 +336,8 @@ def render_rays(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg:
 
     t_rand = rng['t_rand'] if (train and rng is not None and 't_rand' in rng) else None
     z_c = coarse_depths(near, far, cfg['n_coarse'], t_rand, cfg.get('lindisp', False))
+    if rng is not None and rng.get('z_coarse') is not None:
+        z_c = rng['z_coarse']                         # teacher forcing (the float64 row reference): the given coarse depths
     comp_c = level_pass('coarse', z_c, rng['noise_coarse'] if use_noise else None)
     if cfg.get('n_fine', 0) > 0:
         u = rng['u'] if (train and rng is not None and 'u' in rng) else None
@@ -370,7 +378,7 @@ def loss_visibility_prior(batch, out, levels):
     elif 'visibility_prior_weights' in batch:
         pw = batch['visibility_prior_weights']
     else:
-        pw = torch.ones((batch['rays_o'].shape[0], int(batch['num_frames']) - 1))
+        pw = torch.ones((batch['rays_o'].shape[0], int(batch['num_frames']) - 1), dtype=batch['rays_o'].dtype)
     tot = 0
     for lv in levels:
         v2 = out[f'visibility2_{lv}'][m]
@@ -381,11 +389,11 @@ def loss_visibility_prior(batch, out, levels):
 
 def loss_sparse_depth(batch, out, levels):
     if 'indices_mask_sparse_depth' not in batch:
-        return torch.zeros(())
+        return torch.zeros((), dtype=batch['rays_o'].dtype)
     m = batch['indices_mask_sparse_depth']
     lv = 'fine' if 'fine' in levels else 'coarse'
     e = out[f'depth_{lv}'][m] - batch['sparse_depth_values'][:, 0][m]
-    return torch.mean(torch.square(e)) if e.numel() > 0 else torch.zeros(())
+    return torch.mean(torch.square(e)) if e.numel() > 0 else torch.zeros((), dtype=e.dtype)
 
 
 def schedule_weight(loss_cfg: dict, iter_num: int) -> float:

@@ -169,3 +169,47 @@ def test_16bit_training_refuses_point_counts_that_are_not_whole_tiles():
     cfg_o = {'ndc': b['ndc'], 'n_coarse': nco, 'n_fine': nfi, 'noise_std': 1.0, 'white_bkgd': False, 'lindisp': False}
     with pytest.raises(VipNerfHipError, match='multiple of (16|32)'):
         r2._oracle_and_hip_step(dev, b, vo.init_params(304, scale=1.6), vo.synthetic_rng(n, nco, nfi, 305), {}, cfg_o, prec='bf16')
+
+
+@pytest.mark.parametrize('n_rows', [8193, 65536])
+def test_visibility_losses_at_size_vs_float64(n_rows):
+    """VisibilityLoss and VisibilityPriorLoss of vipnerf_losses_forward -- values and seeds -- against a float64 evaluation of their definitions
+    on the same inputs, at sizes past one workgroup's inline mask count (8192 rows) with sparse-depth rows in the batch: VisibilityLoss01.py
+    (the mean over ALL rows and samples of |T^ - T|, twice: once per detached side; seeds sign(T^ - T) / (N S)) and VisibilityPriorLoss01.py
+    (the mean over the nerf rows of sum_v w_v (1 - v2_v); seeds -w_v / n_nerf on nerf rows, 0 elsewhere)."""
+    from vipnerf_hip import ops
+    dev = torch.device('cuda:0')
+    g = torch.Generator(device='cpu').manual_seed(n_rows + 1)
+    n_nerf, V = n_rows - 1111, 2
+    mask_nerf = torch.arange(n_rows) < n_nerf
+    tgt = torch.rand(n_rows, 3, generator=g)
+    prior = (torch.rand(n_rows, V, generator=g) < 0.5).float()
+    sd = torch.rand(n_rows, generator=g) * 4
+    cfg = ops.make_config(True, 64, 128, V, False)
+    lv_in = {}
+
+    def lvl(S):
+        d = {'rgb': torch.rand(n_rows, 3, generator=g), 'visibility': torch.rand(n_rows, S, generator=g), 'raw_vis': torch.rand(n_rows, S, generator=g),
+             'vis2': torch.rand(n_rows, V, generator=g), 'depth': torch.rand(n_rows, generator=g) * 4}
+        lv_in[S] = d
+        return {k: v.to(dev) for k, v in d.items()}
+    coarse, fine = lvl(64), lvl(192)
+    vals, sc, sf = ops.losses_forward(cfg, n_rows, tgt.to(dev), mask_nerf.to(dev), prior.to(dev), ~mask_nerf.to(dev), sd.to(dev), coarse, fine)
+    v = vals.cpu().double()
+    worst_v, worst_s = 0.0, 0.0
+    for li, (S, seeds) in enumerate(((64, sc), (192, sf))):
+        d = {k: t.double() for k, t in lv_in[S].items()}
+        diff = d['raw_vis'] - d['visibility']
+        ref_vis = 2 * diff.abs().mean()
+        ref_prior = (prior.double()[mask_nerf] * (1 - d['vis2'][mask_nerf])).sum(1).mean()
+        for got, ref in ((v[2 + li], ref_vis), (v[4 + li], ref_prior)):
+            e = abs(float(got) - float(ref)) / abs(float(ref))
+            worst_v = max(worst_v, e)
+            assert e <= 2e-6, (li, float(got), float(ref))
+        s_vis = torch.sign(diff) / (n_rows * S)
+        for k, ref in (('raw_vis', s_vis), ('visibility', -s_vis), ('vis2', -prior.double() * mask_nerf[:, None] / n_nerf)):
+            got = seeds[k].cpu().double()
+            e = float((got - ref).abs().max() / ref.abs().max())
+            worst_s = max(worst_s, e)
+            assert e <= 1e-6, (li, k, e)
+    print(f'{n_rows} rows ({n_nerf} nerf): visibility / prior loss values worst rel err {worst_v:.2e}, seeds {worst_s:.2e}')

@@ -164,3 +164,78 @@ def test_trainer_one_call_iterations_equal_the_module_contract():
     assert torch.equal(runs[True][0], runs[False][0]), 'parameters after six iterations differ between the two entry points'
     np.testing.assert_allclose(runs[True][1], runs[False][1], rtol=1e-6)
     np.testing.assert_allclose(runs[True][2], runs[False][2], rtol=1e-6)
+
+
+@pytest.mark.parametrize('nf,nco,nfi', [(4, 8, 24), (3, 5, 11)])
+def test_one_call_step_with_fewer_coarse_samples_than_centre_values(nf, nco, nfi):
+    """3 (n_frames - 1) > n_coarse: k_coarse_z has too few sample threads per ray for the other cameras' centres, so vipnerf_train_step
+    launches the standalone vipnerf_secondary_origins in front (it returned E_ARG before).  Bit for bit the module-contract path, two
+    iterations, fp32, as test_one_call_step_is_the_five_call_step."""
+    import bench
+    from loss_functions.LossComputerHip01 import LossComputerHip
+    from oracle import vipnerf_oracle as vo
+    from vipnerf_hip import ops
+    from vipnerf_hip.step import FusedTrainStep
+    dev = torch.device('cuda:0')
+    assert 3 * (nf - 1) > nco
+
+    def build():
+        from models.ModelFactory import get_model
+        from vipnerf_hip.optim import FlatAdam
+        cfg = bench.model_configs(True)
+        cfg['model']['coarse_mlp']['num_samples'], cfg['model']['fine_mlp']['num_samples'] = nco, nfi
+        torch.manual_seed(11)
+        model = get_model(cfg, None).to(dev).train()
+        return cfg, model, FlatAdam(model.parameters(), lr=5e-4, betas=(0.9, 0.999))
+    cfg_a, model_a, opt_a = build()
+    cfg_b, model_b, opt_b = build()
+    lossc = LossComputerHip(cfg_a)
+    step = FusedTrainStep(model_b, cfg_b, opt_b)
+    for i in range(2):
+        it = 40000 + i
+        b = bench.make_batch_oracle(vo, 96, 700 + i, dev, iter_num=it, scene='fern', nf=nf)
+        ba, bb = _fresh(b, it), _fresh(b, it)
+        for p in model_a.parameters():
+            p.grad = None
+        out_a = model_a(ba)
+        lossc.compute_losses(ba, out_a)['TotalLoss'].backward()
+        grad_a = torch.cat([p.grad.flatten() for p in model_a.parameters()]).clone()
+        opt_a.step()
+        step(bb)
+        torch.cuda.synchronize()
+        o = step.outputs
+        assert o['vis2_fine'].shape[-1] == nf - 1
+        for k in OUT_KEYS:
+            ka = {'vis2_fine': 'visibility2_fine'}.get(k, k)
+            assert torch.equal(o[k].reshape(-1), out_a[ka].detach().reshape(-1)), f'{nf} frames {nco}+{nfi} iter {i}: output {k} differs'
+        B = next(reversed(step._bufs.values()))
+        assert torch.equal(B.o2, ops.secondary_origins(bb['common_data']['poses'], bb['pixel_id'], nf))
+        grad_b = torch.cat([p.grad.flatten() for p in model_b.parameters()])
+        assert float(grad_a.abs().max()) > 0 and torch.equal(grad_a, grad_b), f'iter {i}: gradients differ'
+        assert torch.equal(opt_a.flat, opt_b.flat) and torch.equal(opt_a.exp_avg_sq, opt_b.exp_avg_sq) and opt_a.t == opt_b.t
+
+
+def test_one_call_step_refuses_a_16bit_level_that_is_not_whole_tiles_up_front():
+    """A 16-bit level whose rays x samples is 16 (mod 32) passes pack, forward and the losses and used to be refused only in render_backward,
+    in the middle of the step.  vipnerf_train_step now refuses it before any launch, naming the level and the point count: parameters, Adam
+    moments and t are untouched.  (16 rays x 64 + 127 samples: coarse 1024 points, fine 3056 = 16 mod 32.)"""
+    import bench
+    from oracle import vipnerf_oracle as vo
+    from vipnerf_hip import _lib as L
+    from vipnerf_hip.step import FusedTrainStep
+    from models.ModelFactory import get_model
+    from vipnerf_hip.optim import FlatAdam
+    dev = torch.device('cuda:0')
+    cfg = bench.model_configs(True)
+    cfg['model']['fine_mlp']['num_samples'] = 127
+    cfg['model']['hip_precision'] = 'bf16'
+    torch.manual_seed(11)
+    model = get_model(cfg, None).to(dev).train()
+    opt = FlatAdam(model.parameters(), lr=5e-4, betas=(0.9, 0.999))
+    step = FusedTrainStep(model, cfg, opt)
+    b = bench.make_batch_oracle(vo, 16, 701, dev, scene='fern', nf=2)
+    flat, m1, m2, t = opt.flat.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(), opt.t
+    with pytest.raises(L.VipNerfHipError, match=r"level 'fine' has 3056 points \(rays x samples\), a multiple of 32 is required"):
+        step(_fresh(b, 40000))
+    torch.cuda.synchronize()
+    assert torch.equal(opt.flat, flat) and torch.equal(opt.exp_avg, m1) and torch.equal(opt.exp_avg_sq, m2) and opt.t == t

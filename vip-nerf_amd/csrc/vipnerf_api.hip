@@ -72,7 +72,7 @@ static int check_cfg(const vipnerf_config *cfg) {
     // the per-ray kernels give a lane ceil(S / 64) samples and predicate the tail).  Measured against the oracle for 5 + 11 ... 100 + 156, odd counts
     // and odd ray numbers included (profiles/r06_sample_counts_probe.log).  Limits: <= 256 samples per ray and level (four per lane), >= 2 coarse
     // samples, >= 3 with importance sampling (sample_pdf's bins).  The 16-bit TRAINING kernels additionally need a level's POINT count (rays x
-    // samples) to be a multiple of 32 -- their T16 tile storage -- and say so per call (launch_mlp_fwd_pt2, launch_wgrad16).
+    // samples) to be a multiple of 32 -- their T16 tile storage -- and are refused up front (check_t16_points).
     if (cfg->n_coarse < 2 || cfg->n_coarse > 256) {
         set_error("n_coarse=%d unsupported (2..256)", cfg->n_coarse); return VIPNERF_E_UNSUPPORTED; }
     if (cfg->n_fine < 0 || (cfg->n_fine > 0 && (cfg->n_coarse < 3 || cfg->n_coarse + cfg->n_fine > 256))) {
@@ -110,6 +110,21 @@ static GenTopo cfg_topo(const vipnerf_config *cfg) {
                     cfg->pe_degrees ? ((cfg->pe_degrees >> 8) & 0xff) : LV, cfg->head_variant);
 }
 static bool cfg_generic(const vipnerf_config *cfg) { return !gen_is_fused_topology(cfg_topo(cfg)); }
+// The 16-bit training kernels' T16 tiles: a level's points (rays x samples) must come in whole 32-point blocks (launch_wgrad16).  Checked once,
+// before any launch, by render_forward when it saves activations and by vipnerf_train_step, so that a step is refused up front and not in the
+// middle (the data-gradient kernels alone would accept 16-point multiples).
+static int check_t16_points(const vipnerf_config *cfg, int64_t N) {
+    if (!cfg->save_acts || !stores_t16(cfg->precision) || N <= 0) return VIPNERF_OK;
+    for (int lv = 0; lv < (cfg->n_fine > 0 ? 2 : 1); ++lv) {
+        const int64_t P = N * (int64_t)(lv ? cfg->n_coarse + cfg->n_fine : cfg->n_coarse);
+        if (P % 32) {
+            set_error("16-bit training (precision=%d): level '%s' has %lld points (rays x samples), a multiple of 32 is required", cfg->precision,
+                      lv ? "fine" : "coarse", (long long)P);
+            return VIPNERF_E_UNSUPPORTED;
+        }
+    }
+    return VIPNERF_OK;
+}
 
 int launch_mlp_fwd_bf16n(const MlpFwdArgs &a, int precision, hipStream_t st);
 int launch_mlp_bwd_bf16n(const MlpBwdArgs &a, int precision, hipStream_t st);
@@ -347,6 +362,7 @@ static int32_t render_forward_impl(const vipnerf_config *cfg, const vipnerf_rays
     hipStream_t st = (hipStream_t)stream;
     const int64_t N = rays->n_rays;
     if (N == 0) return VIPNERF_OK;
+    if ((rc = check_t16_points(cfg, N))) return rc;
     const int Sc = cfg->n_coarse, Sf = cfg->n_fine, V = cfg->n_sec;
     const bool train = cfg->train != 0, perturb = cfg->perturb != 0;
     const uint64_t seed = rng ? rng->seed : 0, offset = rng ? rng->offset : 0, ray_base = rng ? rng->ray_base : 0;
@@ -595,20 +611,24 @@ int32_t vipnerf_train_step(const vipnerf_train_step_args *t, vipnerf_stream_t st
     if (t->adam_n < 0 || (t->adam_n > 0 && (!t->adam_param || !t->adam_exp_avg || !t->adam_exp_avg_sq || !t->adam_grad))) {
         set_error("train_step: bad Adam arguments"); return VIPNERF_E_ARG; }
     const int64_t N = t->rays->n_rays;
+    if ((rc = check_t16_points(cfg, N))) return rc;
     // 0. the other cameras' centres of every row (VipNeRF01.py:84-98)
     if (t->poses) {
         if (!t->pixel_id || !t->rays_o2_out || t->rays_o2_out != t->rays->rays_o2) {
             set_error("train_step: poses given, so pixel_id and rays_o2_out (== rays->rays_o2) are needed"); return VIPNERF_E_ARG; }
         if (t->n_frames < 1 || t->n_frames > 1 + VIPNERF_MAX_SEC) { set_error("train_step: n_frames=%d", t->n_frames); return VIPNERF_E_ARG; }
     }
-    // (the centres are written by the step's first launch, k_coarse_z: no launch of their own)
+    // (the centres are written by the step's first launch, k_coarse_z: no launch of their own -- unless a ray has fewer coarse sample threads
+    //  than the 3 (n_frames - 1) values, which then get the standalone launch in front of the forward)
     SecOriginArgs so;
     memset(&so, 0, sizeof(so));
-    if (t->poses && t->n_frames > 1 && N > 0) { so.poses = t->poses; so.pixel_id = t->pixel_id; so.idx64 = t->pixel_id_is_int64; so.nf = t->n_frames; so.rays_o2 = t->rays_o2_out; }
+    const bool so_apart = t->poses && t->n_frames > 1 && N > 0 && 3 * (t->n_frames - 1) > cfg->n_coarse;
+    if (t->poses && t->n_frames > 1 && N > 0 && !so_apart) { so.poses = t->poses; so.pixel_id = t->pixel_id; so.idx64 = t->pixel_id_is_int64; so.nf = t->n_frames; so.rays_o2 = t->rays_o2_out; }
     // 1. this iteration's weights in fragment order
     if (two) {
         if ((rc = vipnerf_pack_weights2_c(cfg, t->params_coarse, t->packed_coarse, t->params_fine, t->packed_fine, stream))) return rc;
     } else if ((rc = vipnerf_pack_weights_c(cfg, t->params_coarse, t->packed_coarse, stream))) return rc;
+    if (so_apart && (rc = vipnerf_secondary_origins(N, t->n_frames, t->poses, t->pixel_id, t->pixel_id_is_int64, t->rays_o2_out, stream))) return rc;
     // 2. forward, 3. losses
     if ((rc = render_forward_impl(cfg, t->rays, t->rng, t->packed_coarse, t->packed_fine, t->out, t->acts, stream, so.rays_o2 ? &so : nullptr))) return rc;
     LossArgs la;
